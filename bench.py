@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- attack iterations/sec of the MI355X hot path, with roofline and CPU-baseline legs.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the one JSON line (headline value, ms_per_step, the device span of
+  kernel A's forward launches inside the timed region); every other leg described below -- the event-timed kernel figures, the
+  BERT-base and read-ceiling probes, live PMC, restarts32, the selection collectives, parity and both baselines -- runs only with
+  --full (their fields are null otherwise).  --dump-outputs DIR writes what the timed path computed in its last step (see
+  dump_outputs) before any of those legs touches the trial state; such a run uses deterministic convolution solvers chosen without
+  timing throughout (see main), so two runs with the same arguments write the same files.
   N > 1: the driver launches it through torch.distributed.run (one rank per GPU); a bare `python bench.py --gpus N` re-launches
   itself the same way.  With fewer GPUs than ranks (a 1-GPU box) the ranks share devices and agree over gloo -- a functional
   check only, flagged "oversubscribed": true.
@@ -149,9 +155,10 @@ def committed_replay_duration(kernel_prefix):
     return None, None
 
 
-def device_record(device):
+def device_record(device, clocks=True):
     """Which GPU and software produced the line (box-to-box differences of a few per cent come with MIOpen's timing-based solver
-    choice on a fresh box and with the board; this is what a reader needs to tell two lines apart)."""
+    choice on a fresh box and with the board; this is what a reader needs to tell two lines apart).  `clocks`: also query the
+    current clock levels (a rocm-smi subprocess; --full runs only)."""
     import torch
 
     try:
@@ -159,6 +166,8 @@ def device_record(device):
         record = dict(name=props.name, arch=getattr(props, "gcnArchName", None), compute_units=props.multi_processor_count,
                       memory_GB=round(props.total_memory / 1e9, 1), torch=torch.__version__, hip=getattr(torch.version, "hip", None))
         try:  # current clock levels, when rocm-smi is there: the first thing to look at when two boxes differ by a few per cent
+            if not clocks:
+                return record
             import shutil
             import subprocess
 
@@ -618,11 +627,42 @@ def restarts32_pool_subprocess(ranks, iters, num_trials, model_name, timeout):
         return dict(error=repr(exc)[:400])
 
 
-def parse_args():
+def dump_outputs(out_dir, trials):
+    """`--dump-outputs DIR`: what the timed path handed back after its last step, per trial in flight on this rank -- the candidate
+    (the tensor kernel B updates in place), the best copy kept by the loss commit, the objective of every step run so far (warm-up
+    and timed) and [last objective, running minimum] -- as DIR/trial<t>_<name>.npy in float32.  `trials` = [(global trial index,
+    FusedTrial)].  A few MB at the headline shape; the inputs are seeded, so two builds run with the same arguments can be compared
+    file by file."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for t, trial in trials:
+        state = trial.read_state()
+        arrays = dict(candidate=trial.candidates[0], best_candidate=trial.best()[0],
+                      loss_history=trial.history[: min(trial.iterations, trial.max_iterations)],
+                      objective=np.array([state["total"], state["minimum"]]))
+        for name, value in arrays.items():
+            host = value.detach().float().cpu().numpy() if hasattr(value, "detach") else value
+            host = np.ascontiguousarray(host, dtype=np.float32)
+            written += host.nbytes
+            np.save(os.path.join(out_dir, f"trial{t}_{name}.npy"), host)
+    assert written <= 64 * 2**20, f"--dump-outputs wrote {written} bytes, more than 64 MB"
+    return written
+
+
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beyond the headline figure (kernel events, roofline probes, live PMC, restarts32, selection "
+                        "collectives, parity, GPU and CPU baselines); a plain run only sets up, warms up, times the steps and prints")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32); the "
+                        "victim's convolutions then run on deterministic MIOpen solvers chosen without timing, so that two runs "
+                        "compute the same outputs (several times slower per step than a plain run)")
     p.add_argument("--cpu-baseline-iters", type=int, default=80,
                    help="timed CPU iterations of the reference (or its port), ~10 s of host work (0 disables)")
     p.add_argument("--cpu-threads", type=int, default=0,
@@ -658,13 +698,35 @@ def parse_args():
                         "subprocess from rank 0 after the other ranks have left")
     p.add_argument("--trials-per-gpu", type=int, default=1,
                    help="independent restarts in flight per GPU on separate streams (BASELINE configs[3]: 32 trials on 8 GPUs = 4)")
-    return p.parse_args()
+    return p.parse_args(argv)
 
 
 def main():
     args = parse_args()
     import torch
     import torch.distributed as dist
+
+    private_db = False
+    if args.dump_outputs:
+        # The victim's convolutions run on MIOpen.  Its default solvers for this workload are not run-to-run reproducible (two eager runs
+        # from a warm solver cache differ from the first iteration on: split-K weight-gradient kernels accumulate with atomics), and
+        # hard-sign Adam turns a 1-ulp difference into another trajectory.  Deterministic solvers alone are not enough either: by default
+        # MIOpen picks among them by timing whenever its user find-db has no entry, and reads earlier runs' entries otherwise, so the
+        # choice depends on the home directory and on the clock.  A run whose outputs are meant for comparison therefore takes
+        # deterministic solvers chosen by MIOpen's heuristics alone (FIND_MODE=FAST) against a user database of its own that starts
+        # empty -- the same choice in every run of the same software on the same GPU -- at several times the plain run's time per step.
+        # A plain run keeps the default solvers; `conv_solvers` in the line says which applied.  MIOpen reads these variables at its
+        # first use, which comes later (build_case); explicit settings of the caller are kept.
+        import atexit
+        import shutil
+        import tempfile
+
+        torch.backends.cudnn.deterministic = True
+        os.environ.setdefault("MIOPEN_FIND_MODE", "FAST")
+        if "MIOPEN_USER_DB_PATH" not in os.environ:
+            os.environ["MIOPEN_USER_DB_PATH"] = tempfile.mkdtemp(prefix="bench_miopen_userdb_")
+            private_db = True
+            atexit.register(shutil.rmtree, os.environ["MIOPEN_USER_DB_PATH"], True)
 
     import breaching_amd
     from breaching_amd import trials
@@ -682,6 +744,7 @@ def main():
         record["device"] = device_record(torch.device("cuda", index))
         print(json.dumps(record), flush=True)
         return
+    kernel_timing = args.full and not args.no_kernel_timing  # event pairs and the probes built on them: --full only
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -821,7 +884,7 @@ def main():
         with open(staged_flag, "w") as f:  # releases the other ranks of the staged start (above)
             f.write("warm\n")
     plan = attacker.objective._plan
-    timed_with_events = plan is not None and not args.no_kernel_timing and run.graph is None
+    timed_with_events = plan is not None and kernel_timing and run.graph is None
     if timed_with_events:
         plan.enable_timing()  # eager timed region: the events ride inside it
     if plan is not None:
@@ -851,11 +914,13 @@ def main():
         elapsed = float(t.item())
     mode = "hipGraph replay" if run.graph is not None else "eager launches"
     graph_failed = run.graph_failed
+    if args.dump_outputs:  # before any later leg steps the trials on
+        dump_outputs(args.dump_outputs, [(rank, run)] + [(rank + world * j, other) for j, (_, other) in enumerate(extra, 1)])
 
     # A replayed graph cannot carry host-visible event pairs, so when the timed region ran as graph replays the same
     # iteration body is continued eagerly for a few more steps with a HIP event pair around every kernel-A launch.
     eager_ms = None
-    if plan is not None and not args.no_kernel_timing and not timed_with_events:
+    if plan is not None and kernel_timing and not timed_with_events:
         run.disable_graph()
         with torch.cuda.stream(first_stream):
             for _ in range(3):
@@ -925,13 +990,13 @@ def main():
                         frac=round(achieved / HBM_PEAK_GBS, 4), traffic=pmc_traffic_bytes("gm_fwd_kernel"),
                         avg_launch_us=round(span_us, 2), launches=span_launches, algorithmic_bytes=fwd_bytes,
                         measured="device wall clock (first workgroup in -> last workgroup out) of every launch in the timed region")
-    if roofline is not None and rank == 0 and world == 1 and not args.no_hbm_resident and not args.no_kernel_timing:
+    if roofline is not None and rank == 0 and world == 1 and not args.no_hbm_resident and kernel_timing:
         try:
             with torch.cuda.stream(first_stream):
                 roofline["hbm_resident"] = hbm_resident_leg(device)
         except Exception as exc:  # e.g. out of memory next to another tenant: reported, never fatal for the headline value
             roofline["hbm_resident"] = dict(error=repr(exc))
-    if roofline is not None and "fwd" in kernels and rank == 0 and world == 1 and not args.no_kernel_timing:
+    if roofline is not None and "fwd" in kernels and rank == 0 and world == 1 and kernel_timing:
         try:
             with torch.cuda.stream(first_stream):
                 roofline["ceiling"] = read_ceiling_leg(device, n_elements, kernels["fwd"]["avg_us"])
@@ -940,7 +1005,7 @@ def main():
         except Exception as exc:  # the diagnostic library is not part of the product: its absence never fails the bench
             roofline["ceiling"] = dict(error=repr(exc)[:300])
     live = None
-    if roofline is not None and rank == 0 and world == 1 and not args.no_live_pmc and not args.no_kernel_timing and args.model in ("resnet18", "resnet50"):
+    if roofline is not None and rank == 0 and world == 1 and not args.no_live_pmc and kernel_timing and args.model in ("resnet18", "resnet50"):
         live = pmc_traffic_live(args.model)
         if live and "gm_fwd_kernel" in live:
             roofline["traffic"] = live["gm_fwd_kernel"]
@@ -954,7 +1019,7 @@ def main():
     # ---- trial selection: the one collective of the multi-GPU path --------------------------------------------------
     select_ms = score_ms = None
     state = run.read_state()
-    if world > 1:
+    if world > 1 and args.full:
         torch.cuda.synchronize(device)
         ts = time.perf_counter()
         shard = trials.TrialShard.current(world)
@@ -969,7 +1034,7 @@ def main():
 
     # ---- BASELINE configs[3] through the product entry, one GPU: 8 groups of 4 trials in flight (after the timed region) ------
     restarts32 = None
-    if world == 1 and args.restarts32_iters > 0 and args.model == "resnet18":
+    if args.full and world == 1 and args.restarts32_iters > 0 and args.model == "resnet18":
         try:
             restarts32 = restarts32_leg(device, args.model, args.restarts32_iters, args.restarts32_trials)
         except Exception as exc:  # reported, never fatal for the headline value
@@ -977,7 +1042,7 @@ def main():
 
     # ---- N = 1: the selection collectives through a one-rank RCCL communicator (bounded subprocess, off the timed region) ---
     rccl_dry_run = None
-    if world == 1 and not args.no_dry_collective:
+    if args.full and world == 1 and not args.no_dry_collective:
         import subprocess
 
         try:
@@ -991,12 +1056,12 @@ def main():
 
     # ---- parity of the timed configuration + the same-GPU PyTorch baseline (rank 0, N == 1 only; after the timed region) -----
     parity = gpu_torch_baseline = None
-    if rank == 0 and world == 1 and not args.no_parity:
+    if args.full and rank == 0 and world == 1 and not args.no_parity:
         try:
             parity = parity_leg(device, args.model)
         except Exception as exc:
             parity = dict(error=repr(exc)[:300])
-    if rank == 0 and world == 1 and args.gpu_torch_baseline_iters > 0:
+    if args.full and rank == 0 and world == 1 and args.gpu_torch_baseline_iters > 0:
         try:
             gpu_torch_baseline = gpu_torch_baseline_leg(device, args.model, args.gpu_torch_baseline_iters)
         except Exception as exc:
@@ -1004,12 +1069,12 @@ def main():
 
     # ---- CPU baseline (rank 0, N == 1 only) ---------------------------------------------------------------------------
     cpu_baseline = None
-    if rank == 0 and world == 1 and args.cpu_baseline_iters > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline_iters > 0:
         cpu_baseline = cpu_baseline_leg(args.model, args.cpu_baseline_iters, args.cpu_threads)
 
     if world > 1:
         dist.destroy_process_group()  # ranks > 0 are done: they leave, and with them their hold on the other GPUs
-    if rank == 0 and world > 1 and args.restarts32_iters > 0 and args.model == "resnet18":
+    if args.full and rank == 0 and world > 1 and args.restarts32_iters > 0 and args.model == "resnet18":
         # BASELINE configs[3] as north_star states it: the 32 restarts over the N GPUs through the product's single-process entry
         # (TrialWorkerPool over RCCL), in a bounded process of its own -- a failure or a time-out is a record, never a lost line
         restarts32 = restarts32_pool_subprocess(world, args.restarts32_iters, args.restarts32_trials, args.model, timeout=900)
@@ -1051,7 +1116,9 @@ def main():
             "rccl_dry_run": rccl_dry_run,
             "collective_backend": backend if world > 1 else None,
             "oversubscribed": bool(oversubscribed),
-            "device": device_record(device),
+            "device": device_record(device, clocks=args.full),
+            "conv_solvers": (dict(deterministic=True, find_mode=os.environ.get("MIOPEN_FIND_MODE"), user_db="private to this run" if private_db else os.environ.get("MIOPEN_USER_DB_PATH"))
+                             if args.dump_outputs else dict(deterministic=False, find_mode="MIOpen default", user_db="MIOpen default")),
             "staged_start": None if world == 1 else dict(how="rank 0 warms up first; ranks > 0 wait for its file flag (bounded) and start from a copy "
                                                              "of its MIOpen find-db", ranks=staged[1:]),
         }

@@ -39,17 +39,17 @@ stepprior() {
   BREACH_HIP_LIB=$PREV timeout 120 python scripts/step_prior_probe.py >> $OUT/${TAG}_step_prior_probe.jsonl 2>> $OUT/${TAG}_step_prior_probe.err
   cut -c1-330 $OUT/${TAG}_step_prior_probe.jsonl; tail -2 $OUT/${TAG}_step_prior_probe.err | cut -c1-300
 }
-bench_driver() { timeout 600 $B --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_driver_style.json 2> $OUT/${TAG}_bench_driver_style.err; cut -c1-600 $OUT/${TAG}_bench_driver_style.json; tail -2 $OUT/${TAG}_bench_driver_style.err | cut -c1-300; }
-bench_n1()     { timeout 600 $B > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err; cut -c1-300 $OUT/${TAG}_bench_n1.json; }
-bench_4()      { timeout 600 $B --trials-per-gpu 4 --cpu-baseline-iters 0 --no-hbm-resident > $OUT/${TAG}_bench_n1_4trials_in_flight.json 2> /dev/null; cut -c1-200 $OUT/${TAG}_bench_n1_4trials_in_flight.json; }
-bench_8ranks() { timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 8 --steps 20 --warmup 5 --restarts32-iters ${POOL_ITERS:-100} > $OUT/${TAG}_bench_8ranks_one_gpu.json 2> $OUT/${TAG}_bench_8ranks_one_gpu.err; tail -1 $OUT/${TAG}_bench_8ranks_one_gpu.json | cut -c1-900; tail -3 $OUT/${TAG}_bench_8ranks_one_gpu.err | cut -c1-300; }
+bench_driver() { timeout 600 $B --gpus 1 --steps 20 --warmup 5 --full > $OUT/${TAG}_bench_driver_style.json 2> $OUT/${TAG}_bench_driver_style.err; cut -c1-600 $OUT/${TAG}_bench_driver_style.json; tail -2 $OUT/${TAG}_bench_driver_style.err | cut -c1-300; }
+bench_n1()     { timeout 600 $B --full > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err; cut -c1-300 $OUT/${TAG}_bench_n1.json; }
+bench_4()      { timeout 600 $B --full --trials-per-gpu 4 --cpu-baseline-iters 0 --no-hbm-resident > $OUT/${TAG}_bench_n1_4trials_in_flight.json 2> /dev/null; cut -c1-200 $OUT/${TAG}_bench_n1_4trials_in_flight.json; }
+bench_8ranks() { timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 8 --steps 20 --warmup 5 --full --restarts32-iters ${POOL_ITERS:-100} > $OUT/${TAG}_bench_8ranks_one_gpu.json 2> $OUT/${TAG}_bench_8ranks_one_gpu.err; tail -1 $OUT/${TAG}_bench_8ranks_one_gpu.json | cut -c1-900; tail -3 $OUT/${TAG}_bench_8ranks_one_gpu.err | cut -c1-300; }
 trace_bench()  {
-  prof 400 bench "" $B --steps 100 --warmup 20 --cpu-baseline-iters 0 --gpu-torch-baseline-iters 0 --no-parity --no-span-timing --no-hbm-resident --no-dry-collective --restarts32-iters 0
+  prof 400 bench "" $B --steps 100 --warmup 20 --full --cpu-baseline-iters 0 --gpu-torch-baseline-iters 0 --no-parity --no-span-timing --no-hbm-resident --no-dry-collective --restarts32-iters 0
   trace=$(ls -S $(find /tmp/prof_${TAG}_bench -name "*kernel_trace.csv") | head -1)
   [ -n "$trace" ] && python scripts/gap_census.py $trace $OUT/${TAG}_1trial_gap_census --iters 60 --skip-tail 45 --label "1 trial, round 6 HEAD" | head -20
 }
 trace_bench_eager() {  # the launch mode bench.py's event-timed roofline iterations run in (a replayed graph cannot carry event pairs)
-  prof 400 bench_eager "" $B --steps 100 --warmup 20 --no-graph --cpu-baseline-iters 0 --gpu-torch-baseline-iters 0 --no-parity --no-span-timing --no-hbm-resident --no-dry-collective --restarts32-iters 0
+  prof 400 bench_eager "" $B --steps 100 --warmup 20 --full --no-graph --cpu-baseline-iters 0 --gpu-torch-baseline-iters 0 --no-parity --no-span-timing --no-hbm-resident --no-dry-collective --restarts32-iters 0
 }
 trace5()   { prof 400 config5_bert_tag "" python $GRAFT_REPO_ROOT/scripts/config_runs.py --only 5; }
 trace3()   { prof 400 config3_resnet50_seethrough "" python $GRAFT_REPO_ROOT/scripts/config_runs.py --only 3; }

@@ -9,6 +9,12 @@ if ROOT not in sys.path:
 
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 
+# breaching_amd/__init__.py sets GPU_MAX_HW_QUEUES=8 only as a default: a launcher that exports its own value (4, HIP's own
+# default) takes precedence, and then the caller's stream holds one of four queues and the side streams of trials in flight
+# share queues -- and compute pipes -- with it and with each other.  The runtime tests measure the stream layout the package is
+# built for, so the suite pins the package's value for itself and the processes it starts, before the HIP runtime initialises.
+os.environ["GPU_MAX_HW_QUEUES"] = "8"
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a ROCm GPU (run with `-m gpu` on the MI355X box)")

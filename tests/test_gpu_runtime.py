@@ -171,12 +171,12 @@ def test_side_streams_fall_back_to_pool_streams_when_the_calibration_cannot_run(
 
 
 def test_bench_line_contract():
-    """`python bench.py` (the driver's entry point) as a subprocess with small counts: ONE JSON line on stdout with the contract's
+    """`python bench.py --full` (the driver's entry point with every leg) as a subprocess with small counts: ONE JSON line on stdout with the contract's
     fields -- BASELINE.json's metric, value = K steps / measured time, n_gpus, dtype of the arithmetic, a workload-naming config --
     and the legs this repository adds to it: `roofline` (HBM bound, frac = achieved / peak, algorithmic bytes of kernel A's forward,
     a measured read `ceiling`), `parity` (teacher-forced evaluation against the reference fixture, ok), `gpu_torch_baseline` (the port
     on the same GPU, slower than the HIP path), `cpu_baseline`."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--cpu-baseline-iters", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--full", "--cpu-baseline-iters", "2",
            "--gpu-torch-baseline-iters", "4", "--roofline-steps", "6", "--no-live-pmc", "--no-hbm-resident", "--no-dry-collective",
            "--restarts32-iters", "12", "--restarts32-trials", "8"]
     proc = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -211,6 +211,41 @@ def test_bench_line_contract():
     assert line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["cores"] >= 1 and line["cpu_baseline"]["kind"] in ("reference", "port")
     _check_restarts_leg(line["restarts32"], trials=8, iters=12, ranks=1)
     assert line["restarts32"]["pool"] is None and line["restarts32"]["entry"] == "one process, one GPU"
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain `python bench.py --gpus 1 --steps K --warmup W` (no --full): the headline line with K timed steps, none of the legs
+    --full adds, and with --dump-outputs the timed path's state after its last step -- candidate, best copy, the objective of every
+    step -- whose last objective is the line's `final_objective`.  Run twice with the same arguments: the same outputs bit for bit
+    (a dumping run puts the victim's convolutions on deterministic solvers chosen without timing, from a solver database of its own)."""
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "5", "--dump-outputs", str(out)]
+        proc = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        lines = [ln for ln in proc.stdout.splitlines() if ln.strip().startswith("{")]
+        assert len(lines) == 1, proc.stdout[-1000:]
+        line = json.loads(lines[0])
+        with open(os.path.join(ROOT, "BASELINE.json")) as f:
+            assert line["metric"] == json.load(f)["metric"]
+        assert line["unit"] == "attack iterations/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 7
+        assert line["value"] == pytest.approx(7 / (line["ms_per_step"] * 7e-3), rel=1e-3) and line["launch_mode"] == "hipGraph replay"
+        for leg in ("cpu_baseline", "gpu_torch_baseline", "parity", "restarts32", "rccl_dry_run", "eager_ms_per_step"):
+            assert line[leg] is None, leg
+        assert line["kernels"] == {} and "clocks" not in line["device"]
+        assert line["conv_solvers"] == dict(deterministic=True, find_mode="FAST", user_db="private to this run")
+        names = sorted(p.name for p in out.iterdir())
+        assert names == ["trial0_best_candidate.npy", "trial0_candidate.npy", "trial0_loss_history.npy", "trial0_objective.npy"]
+        arrays = {n[len("trial0_"):-4]: np.load(out / n) for n in names}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert arrays["candidate"].shape == arrays["best_candidate"].shape == (1, 3, 224, 224)
+        history = arrays["loss_history"]
+        assert history.shape == (line["warmup"] + 7,) and history[-1] == np.float32(line["final_objective"])
+        assert arrays["objective"][0] == history[-1] and arrays["objective"][1] == history.min()
+        dumps.append(arrays)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 def _check_restarts_leg(leg, trials, iters, ranks):
@@ -263,11 +298,11 @@ def test_bench_restarts_leg_with_eight_pool_ranks_on_one_gpu():
 
 
 def test_bench_multi_rank_launch_on_one_gpu():
-    """`python bench.py --gpus 2` end to end, as the driver's scaling run launches it (torch.distributed.run, one rank per "GPU"; here
+    """`python bench.py --gpus 2 --full` end to end, as the driver's scaling run launches it (torch.distributed.run, one rank per "GPU"; here
     both ranks on cuda:0 over gloo, `oversubscribed`): the staged start through rank 0's file flag (bounded -- no collective holds the
     other ranks), the weak-scaling line, the selection collective, and then -- after the ranks have left -- BASELINE configs[3]
     through the product's TrialWorkerPool in a bounded process of its own (`restarts32`, entry = TrialWorkerPool, 2 ranks)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--restarts32-iters", "8",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--restarts32-iters", "8",
            "--restarts32-trials", "8"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     proc = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=1200, env=env)

@@ -6,6 +6,7 @@ import random
 import socket
 import struct
 
+import numpy as np
 import pytest
 import torch
 
@@ -220,51 +221,34 @@ def test_install_rebinds_the_reference_factory():
         breaching.attacks.OptimizationBasedAttacker, breaching.attacks.OptimizationJointAttacker = original
 
 
-def test_initialisation_schemes_match_reference_bitwise():
-    """Candidate initialisation (base_attack.py:222-285) restated: same seed, same draws, same tensors for every scheme.
-    Runs the method unbound on CPU against the reference's (build container only)."""
-    from oracle.ref_shim import have_reference, import_reference
+HOST_PINNING = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "host_pinning.npz")
+_INIT_SCHEMES = ["randn", "randn-trunc", "rand", "zeros", "red", "green-true", "blue", "dark", "light-true", "rand-patterned-4",
+                 "randn-patterned-8", "patterned-4", "rand-wei-4", "wei-8", "randn-wei-4"]
 
-    if not have_reference():
-        pytest.skip("reference checkout not present")
-    import_reference()
-    from breaching.attacks.base_attack import _BaseAttacker
 
-    from breaching_amd.attacker import HipOptimizationAttacker
+def _initialisation_draws(cls):
+    """`cls._initialize_data` run unbound on CPU for every scheme, seed 0: {scheme: tensor}."""
     from breaching_amd.config import AttrDict
 
     class Holder:
         pass
 
-    schemes = ["randn", "randn-trunc", "rand", "zeros", "red", "green-true", "blue", "dark", "light-true", "rand-patterned-4",
-               "randn-patterned-8", "patterned-4", "rand-wei-4", "wei-8", "randn-wei-4"]
-    for scheme in schemes:
-        drawn = []
-        for cls in (_BaseAttacker, HipOptimizationAttacker):
-            holder = Holder()
-            holder.cfg = AttrDict(init=scheme)
-            holder.setup = dict(device=torch.device("cpu"), dtype=torch.float32)
-            holder.memory_format = torch.contiguous_format
-            holder.dm = torch.tensor([0.4, 0.5, 0.6])[None, :, None, None]
-            holder.ds = torch.tensor([0.2, 0.3, 0.25])[None, :, None, None]
-            torch.manual_seed(0)
-            drawn.append(cls._initialize_data(holder, [2, 3, 10, 12]).detach())
-        assert torch.equal(drawn[0], drawn[1]), scheme
-    holder.cfg = AttrDict(init="nonsense")
-    with pytest.raises(ValueError):
-        HipOptimizationAttacker._initialize_data(holder, [1, 3, 4, 4])
+    drawn = {}
+    for scheme in _INIT_SCHEMES:
+        holder = Holder()
+        holder.cfg = AttrDict(init=scheme)
+        holder.setup = dict(device=torch.device("cpu"), dtype=torch.float32)
+        holder.memory_format = torch.contiguous_format
+        holder.dm = torch.tensor([0.4, 0.5, 0.6])[None, :, None, None]
+        holder.ds = torch.tensor([0.2, 0.3, 0.25])[None, :, None, None]
+        torch.manual_seed(0)
+        drawn[scheme] = cls._initialize_data(holder, [2, 3, 10, 12]).detach()
+    return drawn, holder
 
 
-def test_label_recovery_matches_reference_on_cpu():
-    """Every label strategy, three batch sizes, same seed: identical labels to the reference's
-    `_recover_label_information` (base_attack.py:305-475), random padding included (same CPU draws)."""
-    from oracle.ref_shim import have_reference, import_reference
-
-    if not have_reference():
-        pytest.skip("reference checkout not present")
-    import_reference()
-    from breaching.attacks.base_attack import _BaseAttacker
-
+def _recovered_labels(cls):
+    """`cls._recover_label_information` run unbound on CPU for every strategy and three batch sizes, seed 0:
+    {"<n>_<strategy>": labels}."""
     from breaching_amd.attacker import HipOptimizationAttacker
     from breaching_amd.cases import build_case
     from breaching_amd.config import AttrDict
@@ -273,23 +257,82 @@ def test_label_recovery_matches_reference_on_cpu():
         pass
 
     helpers = ("_labels_idlg", "_labels_analytic", "_labels_yin", "_labels_wainakh_simple", "_labels_bias_corrected")
+    got = {}
     for n in (6, 1, 3):
         case = build_case("convnet", "CIFAR10", n, seed_data=5)
         for strategy in ("iDLG", "analytic", "yin", "wainakh-simple", "bias-corrected", "random"):
-            got = []
-            for cls in (_BaseAttacker, HipOptimizationAttacker):
-                holder = Holder()
-                holder.cfg = AttrDict(label_strategy=strategy)
-                holder.setup = dict(device=torch.device("cpu"), dtype=torch.float32)
-                if cls is HipOptimizationAttacker:
-                    for name in helpers:
-                        fn = getattr(HipOptimizationAttacker, name)
-                        setattr(holder, name, fn.__get__(holder) if name == "_labels_wainakh_simple" else fn)
-                shared = [dict(gradients=[g.clone() for g in d["gradients"]], buffers=None, metadata=dict(d["metadata"], labels=None))
-                          for d in case.shared_data]
-                torch.manual_seed(0)
-                got.append(cls._recover_label_information(holder, shared, case.server_payload, [case.model]))
-            assert torch.equal(got[0], got[1]), (n, strategy)
+            holder = Holder()
+            holder.cfg = AttrDict(label_strategy=strategy)
+            holder.setup = dict(device=torch.device("cpu"), dtype=torch.float32)
+            if cls is HipOptimizationAttacker:
+                for name in helpers:
+                    fn = getattr(HipOptimizationAttacker, name)
+                    setattr(holder, name, fn.__get__(holder) if name == "_labels_wainakh_simple" else fn)
+            shared = [dict(gradients=[g.clone() for g in d["gradients"]], buffers=None, metadata=dict(d["metadata"], labels=None))
+                      for d in case.shared_data]
+            torch.manual_seed(0)
+            got[f"{n}_{strategy}"] = cls._recover_label_information(holder, shared, case.server_payload, [case.model])
+    return got
+
+
+def _reference_host_pinning():
+    """What the unmodified reference returns for the two comparisons above; tests/golden/host_pinning.npz holds this record, so
+    that the tests run where no reference checkout is importable:
+    ``python -c "import tests.test_host_logic as t; t._record_host_pinning()"`` in the build container rewrites it."""
+    from oracle.ref_shim import import_reference
+
+    import_reference()
+    from breaching.attacks.base_attack import _BaseAttacker
+
+    draws, _ = _initialisation_draws(_BaseAttacker)
+    labels = _recovered_labels(_BaseAttacker)
+    return {**{f"init_{k}": v.numpy() for k, v in draws.items()}, **{f"labels_{k}": v.numpy() for k, v in labels.items()}}
+
+
+def _record_host_pinning():
+    np.savez_compressed(HOST_PINNING, **_reference_host_pinning())
+
+
+def _host_pinning_record():
+    """The recorded reference values; where the reference checkout is importable, first checked against it key by key."""
+    from oracle.ref_shim import have_reference
+
+    with np.load(HOST_PINNING) as f:
+        gold = {k: f[k] for k in f.files}
+    if have_reference():
+        live = _reference_host_pinning()
+        assert sorted(live) == sorted(gold)
+        for key, value in live.items():
+            assert value.dtype == gold[key].dtype and np.array_equal(value, gold[key]), key
+    return gold
+
+
+def test_initialisation_schemes_match_reference_bitwise():
+    """Candidate initialisation (base_attack.py:222-285) restated: same seed, same draws, same tensors for every scheme.
+    Runs the method unbound on CPU against the reference's draws (live where the checkout is importable, else its record)."""
+    from breaching_amd.attacker import HipOptimizationAttacker
+    from breaching_amd.config import AttrDict
+
+    gold = _host_pinning_record()
+    drawn, holder = _initialisation_draws(HipOptimizationAttacker)
+    for scheme in _INIT_SCHEMES:
+        assert torch.equal(drawn[scheme], torch.from_numpy(gold[f"init_{scheme}"])), scheme
+    holder.cfg = AttrDict(init="nonsense")
+    with pytest.raises(ValueError):
+        HipOptimizationAttacker._initialize_data(holder, [1, 3, 4, 4])
+
+
+def test_label_recovery_matches_reference_on_cpu():
+    """Every label strategy, three batch sizes, same seed: identical labels to the reference's
+    `_recover_label_information` (base_attack.py:305-475), random padding included (same CPU draws); the reference's labels live
+    where the checkout is importable, else its record."""
+    from breaching_amd.attacker import HipOptimizationAttacker
+
+    gold = _host_pinning_record()
+    got = _recovered_labels(HipOptimizationAttacker)
+    assert sorted(f"labels_{k}" for k in got) == sorted(k for k in gold if k.startswith("labels_"))
+    for key, labels in got.items():
+        assert torch.equal(labels, torch.from_numpy(gold[f"labels_{key}"])), key
 
 
 def _bare_attacker(cls, model, loss_fn, cfg):
@@ -703,6 +746,52 @@ def test_bench_cpu_baseline_is_the_unmodified_reference_when_a_checkout_is_impor
         assert leg["anchor"]["port_over_reference"] == pytest.approx(1.0, abs=0.1) and leg["anchor"]["file"].endswith("cpu_baseline_anchor.json")
     finally:
         torch.set_num_threads(threads)
+
+
+def test_bench_plain_run_is_lean_and_dump_outputs_writes_float32(tmp_path):
+    """bench.py without --full runs only the headline legs (--full is off by default), and `dump_outputs` writes every trial's
+    candidate, best copy, objective history and [last, minimum] objective as float32 .npy files named by the global trial index."""
+    import importlib.util
+    import os
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    args = bench.parse_args(["--gpus", "1", "--steps", "9", "--warmup", "3"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 9 and args.warmup == 3
+    assert bench.parse_args(["--full", "--dump-outputs", str(tmp_path)]).full is True
+
+    class _Trial:  # the attributes of attacker.FusedTrial that dump_outputs reads
+        def __init__(self, seed, iterations):
+            gen = torch.Generator().manual_seed(seed)
+            self.candidates = [torch.randn(1, 3, 8, 8, generator=gen, dtype=torch.float64)]
+            self.iterations, self.max_iterations = iterations, 20
+            self.kept = min(iterations, 20)  # steps beyond max_iterations leave the history as it was
+            self.history = torch.zeros(20)
+            self.history[: self.kept] = torch.rand(self.kept, generator=gen) + 0.5
+            self._best = self.candidates[0] * 0.5
+
+        def best(self):
+            return [self._best]
+
+        def read_state(self):
+            return dict(total=float(self.history[self.kept - 1]), minimum=float(self.history[: self.kept].min()))
+
+    trials = [(0, _Trial(1, 6)), (2, _Trial(2, 25))]
+    written = bench.dump_outputs(str(tmp_path / "out"), trials)
+    names = sorted(os.listdir(tmp_path / "out"))
+    assert names == sorted(f"trial{t}_{n}.npy" for t in (0, 2) for n in ("candidate", "best_candidate", "loss_history", "objective"))
+    assert written == sum(os.path.getsize(tmp_path / "out" / n) - 128 for n in names)  # .npy header: 128 bytes
+    for t, trial in trials:
+        loaded = {n: np.load(tmp_path / "out" / f"trial{t}_{n}.npy") for n in ("candidate", "best_candidate", "loss_history", "objective")}
+        assert all(a.dtype == np.float32 for a in loaded.values())
+        np.testing.assert_array_equal(loaded["candidate"], trial.candidates[0].float().numpy())
+        np.testing.assert_array_equal(loaded["best_candidate"], trial.best()[0].float().numpy())
+        np.testing.assert_array_equal(loaded["loss_history"], trial.history[: trial.kept].numpy())
+        assert loaded["objective"].tolist() == [trial.read_state()["total"], trial.read_state()["minimum"]]
 
 
 def test_gap_census_on_a_synthetic_trace(tmp_path):

@@ -10,7 +10,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 from . import build as _build
 
 # ---- constants mirrored from include/breach_hip.h (checked against the library in tests) -------------------------
-BH_ABI_VERSION = 7
+BH_ABI_VERSION = 8
 BH_GM_CHUNK = 4096
 BH_GM_MAX_PTRS = 448
 BH_GM_PARTIAL_STRIDE = 4
@@ -130,6 +130,7 @@ _PROTOTYPES = {
     "bh_bn_eval_slabs": (c_int32, [c_int32, c_int32, c_int32]),
     "bh_bn_eval_bwd": (c_int, [c_void_p] * 14 + [c_int32, c_int32, c_int32, c_void_p]),
     "bh_bn_eval_bwd_bwd": (c_int, [c_void_p] * 14 + [c_int32, c_int32, c_int32, c_void_p]),
+    "bh_bn_eval_bwd_bwd2": (c_int, [c_void_p] * 15 + [c_int32, c_int32, c_int32, c_void_p]),
     "bh_ln_fwd": (c_int, [c_void_p] * 6 + [c_int32, c_int32, ctypes.c_float, c_void_p]),
     "bh_ln_bwd": (c_int, [c_void_p] * 8 + [c_int32, c_int32, c_void_p]),
     "bh_ln_bwd_bwd": (c_int, [c_void_p] * 12 + [c_int32, c_int32, c_void_p]),

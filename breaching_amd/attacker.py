@@ -25,8 +25,9 @@ from . import _lib, schedules, streams as trial_streams, trials, workers
 from .config import cfg_get as _cfg_get
 from .gm import objective_lookup
 from .priors import HipNormRegularization, HipTotalVariation, launch_tv_norm, regularizer_lookup
-# the HIP layers of the private victim-model copy (kernels E / F) live in their own, frozen module; re-exported here for callers
-from .victim_layers import (FusedEpilogueError, _EvalAffineBatchNorm2d, _EvalBNFunction, _EvalBNGradFunction, _HipLayerNorm,  # noqa: F401
+# the HIP layers of the private victim-model copy (kernels E / F, the convolution gradient node) live in their own module; re-exported
+from .victim_layers import (FusedEpilogueError, _ConvFunction, _ConvGradFunction, _EvalAffineBatchNorm2d, _EvalBNFunction,  # noqa: F401
+                            _EvalBNGradFunction, _HipConv2d, _HipLayerNorm, owned_conv_grad_enabled, use_owned_conv_gradient,
                             _launch_eval_bn, _LayerNormFunction, _LayerNormGradFunction, _PendingBatchNorm, _under_functorch,
                             fast_eval_bn_enabled, fast_eval_bn_mode, fast_layer_norm_enabled, fuse_bn_relu_enabled, fuse_bn_relu_policy,
                             use_affine_eval_batchnorm, use_hip_layernorm)
@@ -208,6 +209,7 @@ class HipOptimizationAttacker:
         timing["total_s"] = time.perf_counter() - t_call
         stats["execution"] = dict(trials=stats.pop("execution_trials"), pool=pool.describe() if pool is not None else None,
                                   fused_epilogue_fallback=getattr(self, "fused_epilogue_fallback", None),
+                                  owned_conv_grad=owned_conv_grad_enabled(self.cfg),
                                   pool_fallback=getattr(self, "_pool_fallback", None), world=shard.world,
                                   trial_streams=trial_streams.calibration_report(self.setup["device"]),
                                   timing={k: round(v, 4) for k, v in timing.items()})
@@ -360,6 +362,8 @@ class HipOptimizationAttacker:
                 use_affine_eval_batchnorm(new_model, bn_mode, fuse_epilogue=fuse_bn_relu_enabled(self.cfg))
             if fast_layer_norm_enabled(self.cfg):
                 use_hip_layernorm(new_model)
+            if owned_conv_grad_enabled(self.cfg):
+                use_owned_conv_gradient(new_model)
             models.append(new_model)
         return models
 

@@ -12,6 +12,8 @@
 //   backward of the backward, for incoming (ggx, ggw, ggb):
 //                  d_gy = ggx * s_c + ggw_c * (inv_c * x - mi_c) + ggb_c ;  d_x = ggw_c * inv_c * gy ;
 //                  d_w_c = inv_c * sum(ggx * gy)
+//                  (ggx may arrive as two terms, ggx + ggx2: behind a convolution it is conv(ggI, W) + conv(I, ggW), and the launch
+//                  reads both instead of an elementwise launch adding them first -- one fp32 add, the rounding that launch had)
 // Optional epilogue (round 4): the residual add and the ReLU that follow the BatchNorm in ResNet blocks ride in the same launches,
 //   forward        z = x * s_c + t_c (+ r) ;  y = relu(z)
 //   backward       gz = gy * [y > 0] ;  gx = gz * s_c ;  gr = gz ;  gw_c, gb_c from gz
@@ -307,7 +309,8 @@ __global__ __launch_bounds__(kBlock) void bn_eval_bwd_kernel(const float* __rest
   }
 }
 
-__global__ __launch_bounds__(kBlock) void bn_eval_bwd_bwd_kernel(const float* __restrict__ ggx, const float* __restrict__ ggw,
+__global__ __launch_bounds__(kBlock) void bn_eval_bwd_bwd_kernel(const float* __restrict__ ggx, const float* __restrict__ ggx2,
+                                                                 const float* __restrict__ ggw,
                                                                  const float* __restrict__ ggb, const float* __restrict__ gy,
                                                                  const float* __restrict__ x, const float* __restrict__ weight,
                                                                  const float* __restrict__ inv_std,
@@ -318,7 +321,7 @@ __global__ __launch_bounds__(kBlock) void bn_eval_bwd_bwd_kernel(const float* __
                                                                  int narrow) {
   __shared__ double lds[bh::kWavesPerBlock];
   const ChannelWalk w = channel_of(C, S, narrow != 0);
-  double v[1] = {0.0};  // sum ggx * gz
+  double v[1] = {0.0};  // sum ggx * gz  (ggx stands for ggx + ggx2 wherever ggx2 is given: one fp32 add before any use)
   if (w.active) {
     const float inv = inv_std[w.c], mi = mean_inv[w.c];
     const float s = (weight ? weight[w.c] : 1.f) * inv;
@@ -341,6 +344,7 @@ __global__ __launch_bounds__(kBlock) void bn_eval_bwd_bwd_kernel(const float* __
     if (vec) {
       const float4* __restrict__ gy4 = reinterpret_cast<const float4*>(gy);
       const float4* __restrict__ ggx4 = reinterpret_cast<const float4*>(ggx);
+      const float4* __restrict__ ggx24 = reinterpret_cast<const float4*>(ggx2);
       const float4* m4 = reinterpret_cast<const float4*>(ymask ? ymask : gy);  // see bn_eval_bwd_kernel
       const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
       const float4* __restrict__ r4 = reinterpret_cast<const float4*>(ggr);
@@ -349,16 +353,17 @@ __global__ __launch_bounds__(kBlock) void bn_eval_bwd_bwd_kernel(const float* __
       const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
       const uint32_t step = (uint32_t)w.lanes;
       for (uint32_t u0 = v0 + (uint32_t)w.lane; u0 < v1; u0 += step * kStage) {
-        float4 gv[kStage], qv[kStage], yv[kStage], xv[kStage], rv[kStage];
+        float4 gv[kStage], qv[kStage], q2v[kStage], yv[kStage], xv[kStage], rv[kStage];
         size_t at[kStage];
 #pragma unroll
         for (int k = 0; k < kStage; ++k) {  // every load of this round before the first use
           const uint32_t u = u0 + (uint32_t)k * step;
           at[k] = slab_offset(u < v1 ? u : u0, B, unit, cstride, cbase);  // past the end: re-read the lane's first element, unused
           gv[k] = gy4[at[k]];
-          qv[k] = xv[k] = rv[k] = zero;
+          qv[k] = q2v[k] = xv[k] = rv[k] = zero;
           yv[k] = m4[at[k]];
           if (ggx) qv[k] = ggx4[at[k]];
+          if (ggx2) q2v[k] = ggx24[at[k]];
           if (d_gy) xv[k] = x4[at[k]];
           if (d_gy && ggr) rv[k] = r4[at[k]];
         }
@@ -367,7 +372,8 @@ __global__ __launch_bounds__(kBlock) void bn_eval_bwd_bwd_kernel(const float* __
           const uint32_t u = u0 + (uint32_t)k * step;
           if (u < v1) {
             float4 g = gv[k];
-            const float4 q = qv[k];
+            float4 q = qv[k];
+            if (ggx2) q = make_float4(q.x + q2v[k].x, q.y + q2v[k].y, q.z + q2v[k].z, q.w + q2v[k].w);  // the add ATen launched
             float4 m = make_float4(1.f, 1.f, 1.f, 1.f);
             if (ymask) {
               m = make_float4(yv[k].x <= 0.f ? 0.f : 1.f, yv[k].y <= 0.f ? 0.f : 1.f, yv[k].z <= 0.f ? 0.f : 1.f, yv[k].w <= 0.f ? 0.f : 1.f);
@@ -394,7 +400,8 @@ __global__ __launch_bounds__(kBlock) void bn_eval_bwd_bwd_kernel(const float* __
       for (uint32_t u = v0 + (uint32_t)w.lane; u < v1; u += (uint32_t)w.lanes) {
         const size_t at = slab_offset(u, B, unit, cstride, cbase);
         float g = gy[at];
-        const float q = ggx ? ggx[at] : 0.f;
+        float q = ggx ? ggx[at] : 0.f;
+        if (ggx2) q = q + ggx2[at];
         const bool on = ymask == nullptr || !(ymask[at] <= 0.f);
         if (!on) g = 0.f;  // gz
         if (d_gy) d_gy[at] = on ? fmaf(q, s, fmaf(kwi, x[at], shift)) + (ggr ? ggr[at] : 0.f) : 0.f;
@@ -491,24 +498,32 @@ int bh_bn_eval_bwd(const float* gy, const float* x, const float* weight, const f
   return bh::launch_status();
 }
 
-int bh_bn_eval_bwd_bwd(const float* ggx, const float* ggw, const float* ggb, const float* gy, const float* x, const float* weight,
-                       const float* inv_std, const float* mean_inv, float* d_gy, float* d_x, float* d_w, double* workspace,
-                       const float* y_mask, const float* gg_residual, int32_t B, int32_t C, int32_t HW, void* stream) {
+int bh_bn_eval_bwd_bwd2(const float* ggx, const float* ggx2, const float* ggw, const float* ggb, const float* gy, const float* x,
+                        const float* weight, const float* inv_std, const float* mean_inv, float* d_gy, float* d_x, float* d_w,
+                        double* workspace, const float* y_mask, const float* gg_residual, int32_t B, int32_t C, int32_t HW, void* stream) {
   if (!eval_bn_args_ok(x, inv_std, mean_inv, B, C, HW) || gy == nullptr) return BH_EINVAL;
+  if (ggx2 != nullptr && ggx == nullptr) return BH_EINVAL;  // a lone term is passed as ggx
   if ((HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(ggx) |
-                         reinterpret_cast<uintptr_t>(d_gy) | reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(y_mask) |
+                         reinterpret_cast<uintptr_t>(ggx2) | reinterpret_cast<uintptr_t>(d_gy) | reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(y_mask) |
                          reinterpret_cast<uintptr_t>(gg_residual)) & 15u) != 0)
     return BH_EINVAL;
   int S = 1, narrow = 0;
   const int grid = eval_bn_grid(B, C, HW, S, narrow);
   if (S > 1 && workspace == nullptr) return BH_EINVAL;
   hipStream_t st = bh::as_stream(stream);
-  hipLaunchKernelGGL(bn_eval_bwd_bwd_kernel, dim3(grid), dim3(kBlock), 0, st, ggx, ggw, ggb, gy, x, weight, inv_std, mean_inv, d_gy,
-                     d_x, d_w, workspace, y_mask, gg_residual, B, C, HW, S, narrow);
+  hipLaunchKernelGGL(bn_eval_bwd_bwd_kernel, dim3(grid), dim3(kBlock), 0, st, ggx, ggx2, ggw, ggb, gy, x, weight, inv_std, mean_inv,
+                     d_gy, d_x, d_w, workspace, y_mask, gg_residual, B, C, HW, S, narrow);
   if (S > 1 && d_w != nullptr)
     hipLaunchKernelGGL(bn_eval_combine_kernel<1>, dim3((C + kBlock - 1) / kBlock), dim3(kBlock), 0, st, workspace, inv_std,
                        mean_inv, d_w, static_cast<float*>(nullptr), C, S);
   return bh::launch_status();
+}
+
+int bh_bn_eval_bwd_bwd(const float* ggx, const float* ggw, const float* ggb, const float* gy, const float* x, const float* weight,
+                       const float* inv_std, const float* mean_inv, float* d_gy, float* d_x, float* d_w, double* workspace,
+                       const float* y_mask, const float* gg_residual, int32_t B, int32_t C, int32_t HW, void* stream) {
+  return bh_bn_eval_bwd_bwd2(ggx, nullptr, ggw, ggb, gy, x, weight, inv_std, mean_inv, d_gy, d_x, d_w, workspace, y_mask, gg_residual,
+                             B, C, HW, stream);
 }
 
 }  // extern "C"

@@ -1,11 +1,13 @@
 """Layers of the attacker's PRIVATE copy of the victim model that run on HIP kernels: eval-mode BatchNorm2d (+ the residual add and
-the ReLU behind it) on kernel E and LayerNorm on kernel F, through both autograd orders the attack differentiates them in.
+the ReLU behind it) on kernel E and LayerNorm on kernel F, through both autograd orders the attack differentiates them in -- and the
+autograd node of Conv2d, which launches no kernel of ours.
 
-This module is the whole of it, and it is FROZEN (SURVEY.md section 8 row a6 "stays PyTorch by design"):
-convolutions in all three autograd orders, GEMMs, pooling, attention, softmax and the loss of the victim model stay PyTorch-ROCm /
-MIOpen / rocBLAS.  What is here exists because, for these two layer types, PyTorch's decomposition of the derivative of the backward
-pass was most of the LAUNCH COUNT of an attack iteration (about 700 of the 1 170 launches of a ResNet-18 iteration, more than half of
-a BERT-base iteration's), not because the arithmetic is the attack's.
+This module is the whole of the victim-model surface (SURVEY.md section 8 row a6 "stays PyTorch by design"):
+the convolutions themselves in all three autograd orders, GEMMs, pooling, attention, softmax and the loss of the victim model stay
+PyTorch-ROCm / MIOpen / rocBLAS.  What is here exists because PyTorch's DECOMPOSITION of the derivative of the backward pass was most
+of an attack iteration -- for BatchNorm and LayerNorm most of the LAUNCH COUNT (about 700 of the 1 170 launches of a ResNet-18
+iteration, more than half of a BERT-base iteration's), for Conv2d a quarter of the KERNEL TIME, spent on a weight gradient that
+nothing reads -- not because the arithmetic is the attack's.
 
   * `use_affine_eval_batchnorm(model, mode, fuse_epilogue)`  -- class swap BatchNorm2d -> `_EvalAffineBatchNorm2d` (same parameters,
     buffers, hooks); `_EvalBNFunction` / `_EvalBNGradFunction` = kernel E's three launches as two chained autograd.Functions;
@@ -13,9 +15,17 @@ a BERT-base iteration's), not because the arithmetic is the attack's.
     `FusedEpilogueError` + `fuse_bn_relu_policy` = the fail-open policy of that fusion (the attacker switches it off on a model it
     cannot serve, attacker.HipOptimizationAttacker._autograd_objective).
   * `use_hip_layernorm(model)`  -- LayerNorm -> `_HipLayerNorm` (kernel F).
+  * `use_owned_conv_gradient(model)`  -- Conv2d -> `_HipConv2d`: `_ConvFunction` / `_ConvGradFunction` call the same ATen
+    convolution ops as before (MIOpen's kernels, unchanged); what changed is which of them the outer pass calls.  ATen's
+    double backward computes the objective's gradient with respect to the victim's WEIGHTS whenever the first-order input gradient
+    exists, although the attack differentiates with respect to the candidate only; the node asks the engine and skips it.  It also
+    hands the second of the two convolution outputs that make up the BatchNorm's incoming gradient to kernel E's second-order
+    launch (bh_bn_eval_bwd_bwd2) instead of adding them with an elementwise launch.  What did not change: every convolution
+    that is needed, its arguments, their order, and therefore every value the attack reads.
 
 reference: none of this exists there -- the reference runs the victim model as it is (objectives.py:36-46); PyTorch's own eval-mode
-batch_norm / layer_norm arithmetic through both orders, run in fp64, is the oracle (tests/test_gpu_kernels.py).
+batch_norm / layer_norm arithmetic through both orders, run in fp64, is the oracle (tests/test_gpu_kernels.py), and the stock Conv2d
+the convolution node's (tests/test_conv_grad.py).
 """
 
 import torch
@@ -152,6 +162,9 @@ class _EvalBNGradFunction(torch.autograd.Function):
         gy, x, weight, inv_std, mean_inv, *rest = ctx.saved_tensors
         mask = rest[0] if ctx.masked else None
         none = (None,) * 9
+        ggx2 = _take_conv_term(ctx)  # the second term of ggx, left here by the convolution that consumed gx (`_ConvGradFunction`)
+        if ggx is None:
+            ggx, ggx2 = ggx2, None
         if ggx is None and ggw is None and ggb is None and ggr is None:
             return none
         if ctx.extra_terms:
@@ -159,6 +172,7 @@ class _EvalBNGradFunction(torch.autograd.Function):
         B, C = x.shape[0], x.shape[1]
         hw = x[0, 0].numel()
         ggx = None if ggx is None else _vector_ready(ggx.to(torch.float32), hw)
+        ggx2 = None if ggx2 is None else _vector_ready(ggx2.to(torch.float32), hw)
         ggr = None if ggr is None else _vector_ready(ggr.to(torch.float32), hw)
         ggw = None if ggw is None else ggw.to(torch.float32).contiguous()
         ggb = None if ggb is None else ggb.to(torch.float32).contiguous()
@@ -170,11 +184,165 @@ class _EvalBNGradFunction(torch.autograd.Function):
         slabs = lib.bh_bn_eval_slabs(B, C, hw)
         ws = torch.empty(C * slabs, dtype=torch.float64, device=x.device) if slabs > 1 else None
         with torch.cuda.device(x.device):
-            _lib.check(lib.bh_bn_eval_bwd_bwd(_lib.ptr(ggx), _lib.ptr(ggw), _lib.ptr(ggb), _lib.ptr(gy), _lib.ptr(x), _lib.ptr(weight),
-                                              _lib.ptr(inv_std), _lib.ptr(mean_inv), _lib.ptr(d_gy), _lib.ptr(d_x), _lib.ptr(d_w),
-                                              _lib.ptr(ws), _lib.ptr(mask), _lib.ptr(ggr), B, C, hw, _lib.current_stream_handle(x.device)),
-                       "bh_bn_eval_bwd_bwd")
+            _lib.check(lib.bh_bn_eval_bwd_bwd2(_lib.ptr(ggx), _lib.ptr(ggx2), _lib.ptr(ggw), _lib.ptr(ggb), _lib.ptr(gy), _lib.ptr(x),
+                                               _lib.ptr(weight), _lib.ptr(inv_std), _lib.ptr(mean_inv), _lib.ptr(d_gy), _lib.ptr(d_x),
+                                               _lib.ptr(d_w), _lib.ptr(ws), _lib.ptr(mask), _lib.ptr(ggr), B, C, hw,
+                                               _lib.current_stream_handle(x.device)), "bh_bn_eval_bwd_bwd2")
         return d_gy, d_x, d_w, None, None, None, None, None, None
+
+
+def _take_conv_term(node):
+    """Pop what `_ConvGradFunction.backward` left on this `_EvalBNGradFunction` node: (graph task id, tensor).  Only an entry of
+    the backward pass that is running now counts; anything else is a leftover of a pass that ended early and is dropped."""
+    entry = getattr(node, "_conv_term", None)
+    if entry is None:
+        return None
+    node._conv_term = None
+    return entry[1] if entry[0] == torch._C._current_graph_task_id() else None
+
+
+def _engine_wants(edge):
+    """Will the backward pass that is running now use the gradient sent along `edge` (an entry of a node's `next_functions`)?
+    `ctx.needs_input_grad` only says `requires_grad`; the engine knows which nodes lie on a path to the `inputs` of this
+    autograd.grad call.  No node: nobody.  The query raises for a leaf that is itself one of those inputs (and outside a backward
+    pass): then the answer is yes -- computing too much is always correct."""
+    node = edge[0] if edge is not None else None
+    if node is None:
+        return False
+    try:
+        return bool(torch._C._will_engine_execute_node(node))
+    except RuntimeError:
+        return True
+
+
+_aten = torch.ops.aten
+
+
+class _ConvFunction(torch.autograd.Function):
+    """y = convolution(x, w, b) -- MIOpen's, through ATen, as before; its backward is `_ConvGradFunction`, one
+    aten.convolution_backward and itself differentiable.  What is owned here is only how the derivative of that backward is
+    decomposed (`_ConvGradFunction.backward`)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride, padding, dilation, groups):
+        ctx.geometry = (list(stride), list(padding), list(dilation), int(groups))
+        ctx.bias_sizes = None if b is None else [w.shape[0]]
+        ctx.save_for_backward(x, w)
+        return _aten.convolution(x, w, b, ctx.geometry[0], ctx.geometry[1], ctx.geometry[2], False, [0] * len(ctx.geometry[0]), groups)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        none = (None,) * 7
+        # the stem's input gradient is not on the way to the parameters: skipped in the first-order pass (ATen's output mask did that)
+        mask = tuple(bool(ctx.needs_input_grad[i]) and _engine_wants(ctx.next_functions[i]) for i in range(3))
+        if not any(mask):
+            return none
+        producer = gy.grad_fn if gy.output_nr == 0 and getattr(gy.grad_fn, "_forward_cls", None) is _EvalBNGradFunction else None
+        gx, gw, gb = _ConvGradFunction.apply(gy, x, w, ctx.geometry, mask, ctx.bias_sizes, producer)
+        return (gx, gw, gb) + none[3:]
+
+
+class _ConvGradFunction(torch.autograd.Function):
+    """(gy, x, w) -> (gx, gw, gb): one aten.convolution_backward with the output mask of what the running pass uses.
+
+    backward = the derivative of that map for incoming (ggx, ggw, ggb), each possibly absent:
+        d_gy = conv(ggx, w) + conv(x, ggw) + ggb          d_x = conv_backward_input(gy, ggw)          d_w = conv_backward_weight(gy, ggx)
+    ATen's `_convolution_double_backward` computes the same three, but d_w whenever ggx is defined -- also when the pass
+    differentiates with respect to the candidate only and the engine has masked that output off, which is every iteration of
+    the attack.  d_w is a convolution of a [C, B, H, W] "input" with a [K, B, H, W] "filter", the shape MIOpen serves worst:
+    about a quarter of a ResNet-18 iteration's kernel time went into a result nobody read.  Here it is launched only when the
+    engine will use it (FedAvg's multi-step updates, whose weights depend on the candidate: gm.py), as a real weight-gradient
+    call.
+
+    `producer`: the `_EvalBNGradFunction` node whose output gy is, when it is one.  In the outer pass d_gy is that node's
+    incoming ggx; instead of adding the two convolution outputs with an elementwise launch, the first is returned and the
+    second is left on the node, whose one launch reads both (bh_bn_eval_bwd_bwd2: the same fp32 add, no launch)."""
+
+    @staticmethod
+    def forward(ctx, gy, x, w, geometry, mask, bias_sizes, producer):
+        stride, padding, dilation, groups = geometry
+        ctx.geometry, ctx.producer = geometry, producer
+        ctx.save_for_backward(gy, x, w)
+        ctx.set_materialize_grads(False)
+        return _aten.convolution_backward(gy, x, w, bias_sizes, stride, padding, dilation, False, [0] * len(stride), groups, list(mask))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, ggx, ggw, ggb):
+        gy, x, w = ctx.saved_tensors
+        stride, padding, dilation, groups = ctx.geometry
+        zeros = [0] * len(stride)
+        want = [bool(ctx.needs_input_grad[i]) and _engine_wants(ctx.next_functions[i]) for i in range(3)]
+        d_gy = d_x = d_w = None
+        if want[0]:
+            t1 = None if ggx is None else _aten.convolution(ggx, w, None, stride, padding, dilation, False, zeros, groups)
+            t2 = None if ggw is None else _aten.convolution(x, ggw, None, stride, padding, dilation, False, zeros, groups)
+            if t1 is not None and t2 is not None:
+                d_gy = t1 if ggb is None and _leave_on_producer(ctx, t2) else t1 + t2
+            else:
+                d_gy = t1 if t2 is None else t2
+            if ggb is not None:
+                bias = ggb.reshape(1, -1, *([1] * (gy.dim() - 2)))
+                d_gy = bias.expand_as(gy) if d_gy is None else d_gy + bias
+        if want[1] and ggw is not None:
+            d_x = _aten.convolution_backward(gy, x, ggw, None, stride, padding, dilation, False, zeros, groups, [True, False, False])[0]
+        if want[2] and ggx is not None:
+            d_w = _aten.convolution_backward(gy, ggx, w, None, stride, padding, dilation, False, zeros, groups, [False, True, False])[1]
+        return d_gy, d_x, d_w, None, None, None, None
+
+
+def _leave_on_producer(ctx, term):
+    """Hand `term`, the second summand of d_gy, to the `_EvalBNGradFunction` node that produced gy, if the running pass will run
+    that node (it then receives the first summand as its ggx from the engine, after this node: it depends on it)."""
+    producer = ctx.producer
+    if producer is None or ctx.next_functions[0] != (producer, 0):
+        return False
+    try:
+        if not torch._C._will_engine_execute_node(producer):
+            return False
+    except RuntimeError:
+        return False
+    task = torch._C._current_graph_task_id()
+    entry = getattr(producer, "_conv_term", None)
+    if entry is not None and entry[0] == task:
+        term = entry[1] + term
+    producer._conv_term = (task, term)
+    return True
+
+
+class _HipConv2d(torch.nn.Conv2d):
+    """torch.nn.Conv2d (same parameters, hooks, `isinstance`; instances converted by swapping ``__class__``) whose forward goes
+    through `_ConvFunction`.  The convolutions of every autograd order are still ATen's / MIOpen's; see `_ConvGradFunction`.
+    Not tied to a device.  Non-zero padding modes, string padding, non-floating or unbatched inputs and torch.func transforms
+    take the stock forward."""
+
+    def forward(self, x):
+        if isinstance(x, _PendingBatchNorm):
+            x = x.value()
+        if (self.padding_mode != "zeros" or isinstance(self.padding, str) or x.dim() != 4 or not x.is_floating_point()
+                or x.dtype != self.weight.dtype or torch.is_autocast_enabled(x.device.type) or _under_functorch(x)):
+            return super().forward(x)
+        return _ConvFunction.apply(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.groups)
+
+
+def use_owned_conv_gradient(model):
+    """Convert every plain Conv2d of `model` in place (idempotent).  On by default; cfg.impl.owned_conv_grad=False or
+    BREACH_HIP_CONV_GRAD=0 keeps the stock modules."""
+    for module in model.modules():
+        if type(module) is torch.nn.Conv2d:
+            module.__class__ = _HipConv2d
+    return model
+
+
+def owned_conv_grad_enabled(cfg):
+    import os
+
+    env = os.environ.get("BREACH_HIP_CONV_GRAD")
+    if env is not None:
+        return env.strip().lower() not in ("0", "false", "off", "no")
+    flag = _cfg_get(cfg.impl, "owned_conv_grad", True)
+    return True if flag is None else bool(flag)
 
 
 def _launch_eval_bn(module, x, sink, tap, residual, relu):

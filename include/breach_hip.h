@@ -25,10 +25,11 @@
 extern "C" {
 #endif
 
-/* 6: multi-tensor launch groups are BH_MT_MAX_PTRS = 112 tensors (two adjacent groups per launch for the forms with at most two
+/* 8: bh_bn_eval_bwd_bwd2 (kernel E's second-order launch adds two incoming terms itself);
+ * 6: multi-tensor launch groups are BH_MT_MAX_PTRS = 112 tensors (two adjacent groups per launch for the forms with at most two
  *    pointer lists), bh_mt_* write outputs larger than the Infinity Cache with non-temporal stores; 5: tuning knobs became launch
  *    arguments (no mutable library state). */
-#define BH_ABI_VERSION 7
+#define BH_ABI_VERSION 8
 #define BH_EINVAL (-1)
 
 /* ------------------------------------------------------------------------------------------------------------------
@@ -302,6 +303,13 @@ int bh_bn_eval_bwd(const float* gy, const float* x, const float* weight, const f
 int bh_bn_eval_bwd_bwd(const float* ggx, const float* ggw, const float* ggb, const float* gy, const float* x, const float* weight,
                        const float* inv_std, const float* mean_inv, float* d_gy, float* d_x, float* d_w, double* workspace,
                        const float* y_mask, const float* gg_residual, int32_t B, int32_t C, int32_t HW, void* stream);
+/* The same launch with the incoming ggx given as two terms: ggx + ggx2 (one fp32 add per element, before any use) takes ggx's place
+ * in d_gy and d_w.  In the attack's outer pass ggx of a BatchNorm behind a convolution is conv(ggI, W) + conv(I, ggW): the kernel
+ * reads both convolution outputs instead of an elementwise launch adding them first, with that launch's rounding.  `ggx2` may be
+ * NULL (= bh_bn_eval_bwd_bwd); without `ggx` it is BH_EINVAL (pass a lone term as ggx); same shape and alignment rule as ggx. */
+int bh_bn_eval_bwd_bwd2(const float* ggx, const float* ggx2, const float* ggw, const float* ggb, const float* gy, const float* x,
+                        const float* weight, const float* inv_std, const float* mean_inv, float* d_gy, float* d_x, float* d_w,
+                        double* workspace, const float* y_mask, const float* gg_residual, int32_t B, int32_t C, int32_t HW, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * LayerNorm over the last dimension (elementwise affine) of the attacker's private model copy, one or two launches per
